@@ -14,8 +14,17 @@ users (MovieLens-25M-like shape) over a shared catalogue of 59,047 items with sk
 popularity; the all-to-all that repartitions ratings by item happens once, before timing.
 
 Prints ONE JSON line (rank 0).  ``value`` = total ratings processed per second over all
-ranks = (global nnz * K) / max-over-ranks(time of K steps).  Extra fields report the
-speed-layer fold-in latency for a 10k-event micro-batch (the second half of the metric).
+ranks = (global nnz * K) / max-over-ranks(time of K steps); ``ms_per_step`` = milliseconds per
+timed step.  A plain run sets up, warms up, times the K steps and prints.
+
+``--dump-outputs DIR`` writes the factors the K-th timed step left (what a caller of the
+trainer receives from ``factors()``) as ``DIR/X.npy`` and ``DIR/Y.npy`` (float32), before
+anything else runs.  The inputs depend only on the arguments, so two builds can be compared
+array for array.
+
+``--full`` adds what takes runs of its own: the per-half-step phase times (3 more iterations
+under events) and the speed-layer fold-in latency for a 10k-event micro-batch (the second half
+of the metric); their fields are null in a plain run.
 """
 
 from __future__ import annotations
@@ -92,6 +101,32 @@ def exchange_schedule(trainer, halfstep_ms: dict, W: int, elem: int) -> dict:
     out["push_ms_per_iteration"] = out["items_push_ms"] + out["users_push_ms"]
     out["ring_ms_per_iteration"] = out["items_ring_ms"] + out["users_ring_ms"]
     return out
+
+
+# --dump-outputs writes at most this many bytes over all arrays; larger outputs are sampled
+DUMP_BUDGET_BYTES = 60_000_000
+
+
+def dump_outputs(directory: str, arrays: dict, seed: int) -> dict:
+    """Writes each 2-D tensor of ``arrays`` as ``directory/<name>.npy`` (float32).  When they
+    exceed DUMP_BUDGET_BYTES together, every array keeps the same fraction of its rows: a
+    sorted sample drawn without replacement from a generator seeded by ``seed`` and the
+    array's position, so equal arguments pick equal rows.  Returns {name: rows written}."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    total = sum(a.numel() * 4 for a in arrays.values())
+    frac = min(1.0, DUMP_BUDGET_BYTES / max(1, total))
+    written = {}
+    for pos, (name, a) in enumerate(arrays.items()):
+        n = a.shape[0]
+        keep = n if frac >= 1.0 else max(1, int(n * frac))
+        if keep < n:
+            rows = np.sort(np.random.default_rng([seed, pos]).choice(n, keep, replace=False))
+            a = a.index_select(0, torch.from_numpy(rows).to(a.device))
+        np.save(os.path.join(directory, name + ".npy"),
+                a.detach().to(torch.float32).cpu().numpy())
+        written[name] = keep
+    return written
 
 
 def emulate(args) -> int:
@@ -208,7 +243,17 @@ def main(argv=None) -> int:
                          "half-steps with collectives that move nothing, and reports their "
                          "times plus the bytes each collective would move")
     ap.add_argument("--emulate-rank", type=int, default=0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the factors they left as DIR/X.npy and "
+                         "DIR/Y.npy (float32; a fixed seeded sample of the rows when the two "
+                         "exceed %d MB)" % (DUMP_BUDGET_BYTES // 1_000_000))
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the per-half-step phases (3 more iterations) and the "
+                         "speed-layer update latency (--speed-events); a plain run only times "
+                         "the steps")
     args = ap.parse_args(argv)
+    if args.dump_outputs and args.emulate_world > 1:
+        ap.error("--dump-outputs is not available with --emulate-world")
     for key, val in PRESETS[args.preset].items():
         if getattr(args, key) is None:
             setattr(args, key, val)
@@ -266,9 +311,18 @@ def main(argv=None) -> int:
     ms_per_step = elapsed * 1e3 / max(1, args.steps)
     ratings_per_sec = global_nnz * args.steps / elapsed
 
+    # what the last timed step left, before anything below runs more iterations (factors()
+    # is a collective: every rank calls it, rank 0 writes)
+    dumped = None
+    if args.dump_outputs:
+        f = trainer.factors()
+        if ctx.is_main:
+            dumped = dump_outputs(args.dump_outputs, {"X": f.X, "Y": f.Y}, args.seed)
+        del f
+
     # per-half-step phases (Gramian + YtY all-reduce / solve / exposed factor exchange) from
     # CUDA events over 3 extra iterations -- untimed, for diagnosing scaling runs
-    halfstep_ms = trainer.phase_breakdown(3)
+    halfstep_ms = trainer.phase_breakdown(3) if args.full else None
 
     # ---- speed layer: one micro-batch of new events through the real speed-layer update
     # (ALSSpeedModelManager.build_updates: native parse, aggregation, Gramian inverses, the
@@ -277,8 +331,9 @@ def main(argv=None) -> int:
     # median and p90 over 12 repetitions after 2 warm-ups (rank 0's GPU)
     speed_ms = speed_p90 = foldin_ms = speed_phases = n_updates = None
     # full factors on every rank (a collective), used by rank 0's speed-layer model
-    f = trainer.factors() if args.speed_events > 0 else None
-    if ctx.is_main and args.speed_events > 0:
+    speed = args.full and args.speed_events > 0
+    f = trainer.factors() if speed else None
+    if ctx.is_main and speed:
         import numpy as np
         from oryx_amd.api import Dataset
         from oryx_amd.models.als.speed import ALSSpeedModel, ALSSpeedModelManager
@@ -394,6 +449,8 @@ def main(argv=None) -> int:
                                 "12",
             "solve_failures": trainer.failures,
             "gather_chunks": {"items": trainer.lay_i.C, "users": trainer.lay_u.C},
+            "full": bool(args.full),
+            "dumped_rows": dumped,
         }
         print(json.dumps(rec), flush=True)
     if ctx.is_distributed:

@@ -18,6 +18,8 @@ if [ "${1:-}" != "--gpu" ]; then
 fi
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread > gpurun_out/final_pytest_gpu.log 2>&1 || { echo tests failed; tail -40 gpurun_out/final_pytest_gpu.log; exit 1; }
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > gpurun_out/final_smoke.log 2>&1 || { tail -20 gpurun_out/final_smoke.log; exit 1; }
-timeout -k 10 400 python -u bench.py > gpurun_out/final_bench.json 2> gpurun_out/final_bench.err || exit 1
+BENCH_OUT=${BENCH_OUT:-bench_out}
+mkdir -p "$BENCH_OUT"
+timeout -k 10 600 python -u bench.py --full > "$BENCH_OUT"/final_bench.json 2> "$BENCH_OUT"/final_bench.err || exit 1
 timeout -k 10 400 python -u bench_rdf.py > gpurun_out/final_bench_rdf.json 2> gpurun_out/final_bench_rdf.err || exit 1
 echo done

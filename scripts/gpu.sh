@@ -9,7 +9,8 @@
 #
 #   tests[=EXPR]        pytest -m gpu (EXPR: a -k expression)
 #   smoke               __graft_entry__.smoke()
-#   bench[=ARGS]        bench.py --steps 20 --warmup 5 [ARGS, comma separated]
+#   bench[=ARGS]        bench.py --full --steps 20 --warmup 5 [ARGS, comma separated], with the
+#                       speed layer and the half-step phases; JSON to $BENCH_OUT (bench_out/)
 #   halfstep[=V]        scripts/als_kernel_bench.py (per half-step ms) with ORYX_ALS_VARIANT=V
 #   hs[=ARGS]           scripts/als_kernel_bench.py ARGS (e.g. hs=--rank-k,128,--precision,fp32);
 #                       ORYX_KERNELS_SO / ORYX_ALS_* from the environment (A/B of builds)
@@ -27,6 +28,8 @@ set -o pipefail
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 export TMPDIR=/tmp
+BENCH_OUT=${BENCH_OUT:-bench_out}
+mkdir -p "$BENCH_OUT"
 PYTEST="python -u -m pytest -x -v --timeout 150 --timeout-method thread"
 
 fail() { echo "== FAILED: $1"; tail -30 "$2"; exit 1; }
@@ -52,8 +55,8 @@ for step in "$@"; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $out 2>&1 || fail "$step" $out
       tail -2 $out ;;
     bench)
-      out=gpurun_out/bench${val:+_$(tag "$val")}${ORYX_FORCE_COLLECTIVES:+_forced}.json
-      timeout -k 10 600 python -u bench.py --steps 20 --warmup 5 $(args "$val") > $out 2> gpurun_out/bench.err || fail "$step" gpurun_out/bench.err
+      out=$BENCH_OUT/bench${val:+_$(tag "$val")}${ORYX_FORCE_COLLECTIVES:+_forced}.json
+      timeout -k 10 600 python -u bench.py --full --steps 20 --warmup 5 $(args "$val") > $out 2> $BENCH_OUT/bench.err || fail "$step" $BENCH_OUT/bench.err
       tail -1 $out | cut -c1-3000 ;;
     halfstep)
       out=gpurun_out/halfstep_v${val:-default}.json

@@ -12,7 +12,8 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SMALL = ["--device", "cpu", "--ratings-per-gpu", "20000", "--users-per-gpu", "500", "--items",
-         "300", "--rank-k", "16", "--steps", "1", "--warmup", "1", "--speed-events", "100"]
+         "300", "--rank-k", "16", "--steps", "1", "--warmup", "1", "--speed-events", "100",
+         "--full"]
 
 
 def _free_port():
@@ -49,6 +50,67 @@ def test_bench_single_process_cpu():
     recs = _json_lines(out.stdout)
     assert len(recs) == 1
     _check(recs[0], 1)
+    assert recs[0]["full"] is True and recs[0]["speed_layer_update_ms"] > 0
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """Without --full the run only times its steps (the phase and speed-layer fields are
+    null); --dump-outputs writes the factors of the last timed step as float32 .npy files, and
+    a second run with the same arguments starts from the same inputs."""
+    import numpy as np
+    plain = [a for a in SMALL if a != "--full"]
+    plain[plain.index("--steps") + 1] = "2"
+    got = []
+    for d in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + plain +
+                             ["--dump-outputs", str(tmp_path / d)],
+                             capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        recs = _json_lines(out.stdout)
+        assert len(recs) == 1
+        rec = recs[0]
+        assert rec["steps"] == 2 and rec["full"] is False and rec["ms_per_step"] > 0
+        assert rec["halfstep_ms"] is None and rec["speed_layer_update_ms"] is None
+        assert rec["dumped_rows"] == {"X": 500, "Y": 300}
+        assert sorted(os.listdir(tmp_path / d)) == ["X.npy", "Y.npy"]
+        X, Y = np.load(tmp_path / d / "X.npy"), np.load(tmp_path / d / "Y.npy")
+        assert X.dtype == np.float32 and X.shape == (500, 16)
+        assert Y.dtype == np.float32 and Y.shape == (300, 16)
+        assert np.isfinite(X).all() and np.isfinite(Y).all() and np.abs(Y).max() > 0
+        got.append((X, Y))
+    # same inputs, same arithmetic up to the order of fp32 sums: the relative difference of
+    # the factor matrices stays far below the 1e-3 that different inputs could not meet
+    for a, b in zip(got[0], got[1]):
+        assert np.linalg.norm(a - b) <= 1e-3 * np.linalg.norm(a)
+
+
+def test_bench_dump_outputs_samples_large_arrays(tmp_path, monkeypatch):
+    """Arrays over the byte budget keep a fixed, seeded sample of their rows."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4000)
+    A = torch.arange(300 * 4, dtype=torch.float32).reshape(300, 4)
+    B = torch.arange(200 * 4, dtype=torch.float64).reshape(200, 4)
+    rows = bench.dump_outputs(str(tmp_path / "a"), {"A": A, "B": B}, seed=7)
+    assert rows == {"A": 150, "B": 100}         # 8000 bytes as float32 -> half of each
+    a, b = np.load(tmp_path / "a" / "A.npy"), np.load(tmp_path / "a" / "B.npy")
+    assert a.dtype == np.float32 and b.dtype == np.float32
+    assert a.nbytes + b.nbytes <= 4000
+    # whole rows of the source, in increasing order, no row twice
+    ia = (a[:, 0] / 4).astype(int)
+    assert (np.diff(ia) > 0).all() and np.array_equal(a, A.numpy()[ia])
+    # the same seed picks the same rows; another seed does not
+    bench.dump_outputs(str(tmp_path / "b"), {"A": A, "B": B}, seed=7)
+    assert np.array_equal(a, np.load(tmp_path / "b" / "A.npy"))
+    bench.dump_outputs(str(tmp_path / "c"), {"A": A, "B": B}, seed=8)
+    assert not np.array_equal(a, np.load(tmp_path / "c" / "A.npy"))
+    # under the budget everything is written
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 8000)
+    assert bench.dump_outputs(str(tmp_path / "d"), {"A": A, "B": B}, seed=7) == \
+        {"A": 300, "B": 200}
 
 
 @pytest.mark.timeout(600)

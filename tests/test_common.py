@@ -4,7 +4,7 @@ Ports of the reference's ``framework/oryx-common`` and ``framework/oryx-ml`` uni
 TextUtilsTest, VectorMathTest, LinearSystemSolverTest, DoubleWeightedMeanTest, ConfigUtilsTest,
 ConfigToPropertiesTest, PMMLUtilsTest, RandomManagerTest, HyperParamsTest, AutoLockTest,
 AutoReadWriteLockTest, ExecUtilsTest, ClassUtilsTest, IOUtilsTest (paths under
-``/root/reference/framework/*/src/test/java/com/cloudera/oryx/``).
+``framework/*/src/test/java/com/cloudera/oryx/`` of the reference's tree).
 """
 
 import math

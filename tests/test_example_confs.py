@@ -1,5 +1,5 @@
-"""Example configurations: this repo's conf/*.conf and -- when the reference checkout is
-present -- the reference's own app/conf/*.conf (read as text by the HOCON parser; SURVEY.md
+"""Example configurations: this repo's conf/*.conf and the reference's own app/conf/*.conf,
+stored under tests/golden/reference_conf/ (read as text by the HOCON parser; SURVEY.md
 section 5.6 keeps the key names so those files stay valid).  Every configured batch update,
 speed manager and serving manager class loads (Java names through the alias table) and the
 serving resource modules resolve to route tables."""
@@ -17,7 +17,7 @@ from oryx_amd.utils import lang
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OURS = sorted(glob.glob(os.path.join(ROOT, "conf", "*.conf")))
-THEIRS = sorted(glob.glob("/root/reference/app/conf/*.conf"))
+THEIRS = sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "reference_conf", "*.conf")))
 
 
 def _check(path):
@@ -41,7 +41,11 @@ def test_our_example_confs(path):
     assert conf.get_string("oryx.batch.storage.model-dir").startswith("file://")
 
 
-@pytest.mark.skipif(not THEIRS, reason="reference checkout not present")
+def test_reference_example_confs_are_stored():
+    assert [os.path.basename(p) for p in THEIRS] == [
+        "als-example.conf", "kmeans-example.conf", "rdf-example.conf", "wordcount-example.conf"]
+
+
 @pytest.mark.parametrize("path", THEIRS, ids=[os.path.basename(p) for p in THEIRS])
 def test_reference_example_confs_stay_valid(path):
     conf = _check(path)

@@ -141,6 +141,7 @@ def test_batch_layer_als_end_to_end(tmp_path):
         mgr = serving.manager
         while time.time() < deadline and not (
                 mgr.model is not None and mgr._warmed is mgr.model and
+                mgr.warm_s is not None and      # (_warmed is set before the warm-up runs)
                 mgr.model.get_fraction_loaded() >= 1.0 and
                 xids2 <= set(mgr.model.get_all_user_ids())):
             time.sleep(0.05)

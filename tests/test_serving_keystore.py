@@ -7,8 +7,8 @@ serving layer answers over HTTPS on both front ends -- the native one (OpenSSL,
 
 Keystores: a PKCS#12 file made with ``openssl pkcs12 -export``; a JKS file written by the small
 writer below (the JDK key protector and the file digest, the inverse of the native reader);
-and, where the reference tree is present, its own fixture ``oryxtest.jks`` (password
-``oryxpass``), read as data only.
+and the reference's own fixture ``oryxtest.jks`` (password ``oryxpass``), stored as
+``tests/golden/oryxtest.jks`` and read as data only.
 """
 
 import hashlib
@@ -26,7 +26,7 @@ from .test_serving_layer import _get, _layer, _self_signed
 
 HAVE_OPENSSL = any(os.path.exists(os.path.join(d, "openssl"))
                    for d in os.environ.get("PATH", "").split(":"))
-REF_JKS = "/root/reference/framework/oryx-lambda-serving/src/test/resources/oryxtest.jks"
+REF_JKS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "oryxtest.jks")
 
 pytestmark = pytest.mark.skipif(not HAVE_OPENSSL,
                                 reason="no openssl binary to make test certificates")
@@ -137,7 +137,6 @@ def test_keystore_wrong_password_does_not_start(stores, native):
                 "oryx.serving.api.native-http": "true" if native else "false"})
 
 
-@pytest.mark.skipif(not os.path.exists(REF_JKS), reason="reference tree not present")
 def test_reference_fixture_keystore():
     """The reference IT's own keystore (``oryxtest.jks``, password ``oryxpass``) serves HTTPS on
     the native front end with the keystore's certificate."""
